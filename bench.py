@@ -7,13 +7,17 @@ Metric (BASELINE.json): 512-sample frames/s of one full train step (forward + lo
 quantizer, joint "finetune_lpc" step (all scopes trainable, cmrl.py:392-511), batch 128 frames per GPU,
 synthetic 16 kHz frames.  A "step" = one optimizer step over one batch resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no launcher environment starts the N ranks ITSELF: the parent (which never touches
 a GPU: the device count comes from sysfs) runs `python -m torch.distributed.run --standalone --nproc-per-node N bench.py ...` as a
 child process, relays rank 0's JSON line and exits with the child's return code; if the first set of ranks dies before printing,
 one more set of fresh ranks runs without HSA_ENABLE_IPC_MODE_LEGACY (spawn_ranks).
+
+After the untimed set-up steps and W warm-up steps exactly K steps are timed (in up to --passes passes).  --dump-outputs DIR
+then writes what the last of them computed as DIR/<name>.npy (dump_outputs); inputs and initial parameters are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel class of the step (the persistent gated-block
 data-gradient kernel, gated_block_dgrad2_kernel, unless another class takes a larger share), timed live with HIP events on
@@ -43,6 +47,7 @@ MFLOP_PER_FRAME_JOINT = 1428.2           # 2 codecs x 3 x 238.04 MF
 PEAK_F32_MFMA_TFLOPS = 157.3             # MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32 (exact fp32)
 PEAK_BF16_MFMA_TFLOPS = 2500.0           # MI355X_MICROARCH.md: dense bf16 MFMA; the split-operand kernels spend SIX bf16 products
 PEAK_SPLIT6_TFLOPS = PEAK_BF16_MFMA_TFLOPS / 6.0   # per fp32-class product: their algorithmic FLOPs are priced against 1/6 of it
+MIN_PASS_STEPS = 10                      # a timed pass stays long against the idle GPU the synchronize at each of its ends costs
 
 
 def synth_batch(B, rank, device):
@@ -230,6 +235,54 @@ def cpu_baseline(B, x_np, lpc_np, budget_s=24.0):
                        f"of a 1/8/32/{cores}-thread probe); {time.perf_counter() - t_start:.1f} s in all; 1-thread figure: batch 8")
 
 
+def pass_sizes(steps, passes):
+    """--steps K: K timed steps in all, in at most `passes` passes of near-equal length, each of at least MIN_PASS_STEPS steps
+    unless K itself is smaller."""
+    n = max(1, min(passes, steps // MIN_PASS_STEPS))
+    return [steps // n + (i < steps % n) for i in range(n)]
+
+
+DUMP_BYTES = 64 * 10 ** 6           # --dump-outputs: every file together, .npy headers included
+DUMP_HEADER_BYTES = 4096            # reserved per file for its .npy header
+DUMP_SEED = 20200504                # indices of the sample of an array too large for its share
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: write every array (float32, as the step computed it) as d/<name>.npy.  The files stay within DUMP_BYTES in
+    all: an array larger than its share of what is left is replaced by a fixed, seeded sample of its flat elements (sorted indices,
+    the same for the same arguments on every run).  Returns {name: (shape written, whole)}."""
+    os.makedirs(d, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].size)
+    left = DUMP_BYTES - DUMP_HEADER_BYTES * len(items)
+    out = {}
+    for i, (name, a) in enumerate(items):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        share = left // (len(items) - i)
+        whole = a.nbytes <= share
+        if not whole:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
+        left -= a.nbytes
+        out[name] = (a.shape, whole)
+    return out
+
+
+def step_outputs(eng, terms):
+    """What a caller of the timed step receives after it: the loss terms train_step returns, the decoded frames of its forward pass,
+    the gradients it computed and the parameters its Adam update left (flat buffers, the engine's layout).  A replayed hipGraph
+    writes the same buffers the captured call returned."""
+    t = {"decoded": eng.decoded, "loss_time": terms["time"], "loss_freq": terms["freq"], "params": eng.params, "grads": eng.grads}
+    for c, q, e in zip(eng.codecs, terms["quan"], terms["ent"]):
+        t[f"loss_quan_{c.scope}"] = q
+        t[f"entropy_{c.scope}"] = e
+    if terms.get("quan_lpc") is not None:
+        t["loss_quan_lpc"] = terms["quan_lpc"]
+    if terms.get("ent_lpc") is not None:
+        t["entropy_lpc"] = terms["ent_lpc"]
+    return {k: v.detach().cpu().numpy() for k, v in t.items()}
+
+
 class _NullComm:
     """--dp-selftest: the data-parallel control flow of one rank with every collective a no-op (prices the segmentation)."""
     world, rank = 1, 0
@@ -338,7 +391,13 @@ def main():
                     help="arithmetic of the gated blocks' forward and weight gradients: split = bf16 matrix cores on fp32 operands split "
                          "into 3 bf16 pieces, 6 products, fp32 accumulate (the engine's default); exact = the fp32 matrix instruction")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a hipGraph")
-    ap.add_argument("--passes", type=int, default=3, help="timed passes of --steps steps each (value = the median pass)")
+    ap.add_argument("--passes", type=int, default=3,
+                    help="at most this many timed passes the --steps steps are divided into, each of at least %d steps unless --steps is "
+                         "smaller (value = the median pass)" % MIN_PASS_STEPS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (loss terms, decoded frames, gradients, updated "
+                         "parameters) as DIR/<name>.npy in float32, %d MB at most in all (a fixed, seeded sample of a larger array); "
+                         "rank 0 only" % (DUMP_BYTES // 10 ** 6))
     ap.add_argument("--dp-selftest", action="store_true",
                     help="N=1 only: run the data-parallel control flow (segmented hipGraph, collectives as no-ops) to price it")
     ap.add_argument("--dp-overlap", action="store_true",
@@ -356,6 +415,8 @@ def main():
     ap.add_argument("--unfused-dgrad", action="store_true", help="debug: per-conv data-gradient launches instead of one fused kernel per gated block")
     ap.add_argument("--unfused-fwd", action="store_true", help="debug: per-conv forward/backward (no block fusion)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -406,8 +467,10 @@ def main():
     dcomm = comm if comm.world > 1 else (_NullComm() if args.dp_selftest else None)
     eng.dp_overlap = bool(args.dp_overlap)
 
+    last_terms = {}
+
     def step():
-        eng.train_step(xd, xd, cfg, lpc_x=lpcd, comm=dcomm)
+        last_terms.update(eng.train_step(xd, xd, cfg, lpc_x=lpcd, comm=dcomm))
 
     # C-ABI calls of one eager step (kernel dispatches per step come from the rocprof trace: profiles/*_step_timeline.txt)
     from nsc_amd import _lib as _nl, engine as _ne
@@ -482,17 +545,19 @@ def main():
         run()
     torch.cuda.synchronize()
 
+    pass_steps = pass_sizes(args.steps, args.passes)
+
     def timed_passes():
         ms = []
-        for _ in range(max(1, args.passes)):
+        for n in pass_steps:
             comm.barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for _ in range(args.steps):
+            for _ in range(n):
                 run()
             torch.cuda.synchronize()
             comm.barrier()
-            ms.append(1e3 * comm.max_float(time.perf_counter() - t0, dev) / args.steps)
+            ms.append(1e3 * comm.max_float(time.perf_counter() - t0, dev) / n)
         return ms
     pass_ms = timed_passes()
     pair_to = eng.pair_timeouts()            # neighbour waits of the pair launches that timed out in ANY step so far (sticky counter): must be 0
@@ -513,6 +578,12 @@ def main():
         pair_to = eng.pair_timeouts() - to_before
         if pair_to:
             raise SystemExit(f"[bench] {pair_to} neighbour wait(s) timed out with pair launches off: results invalid")
+    # what the last timed step computed, before anything below steps the engine again
+    if args.dump_outputs and comm.rank == 0:
+        done = dump_outputs(args.dump_outputs, step_outputs(eng, last_terms))
+        sampled = [k for k, (_, whole) in done.items() if not whole]
+        print(f"[bench] wrote {len(done)} arrays of the last timed step to {args.dump_outputs}"
+              + (f" (sampled: {', '.join(sampled)})" if sampled else ""), file=sys.stderr)
     ms_step = float(np.median(pass_ms))
     dt = ms_step * 1e-3 * args.steps
     fps = comm.world * B * args.steps / dt
@@ -742,7 +813,7 @@ def main():
             "metric": "512-sample frames/s train step (2-codec CMRL)", "value": round(fps, 1), "unit": "frames/s",
             "n_gpus": comm.world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_step, 3), "ms_per_step_passes": [round(v, 3) for v in pass_ms],
-            "ms_per_step_min": round(min(pass_ms), 3), "timing": f"median of {len(pass_ms)} passes of {args.steps} steps, each bracketed by barrier + synchronize, max over ranks",
+            "ms_per_step_min": round(min(pass_ms), 3), "timing": f"median of {len(pass_ms)} passes ({' + '.join(map(str, pass_steps))} = {args.steps} steps), each bracketed by barrier + synchronize, max over ranks",
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None,
             "dtype": ("f32 (" + " + ".join(n_ for n_, on in (("gated-block forward", eng.split_fwd), ("gated-block weight gradients", eng.split_wgrad_arith),

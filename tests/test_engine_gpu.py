@@ -612,3 +612,37 @@ def test_bench_survives_a_pair_launch_timeout(when):
     c = d["config"]
     assert c["pair_launches"] is False and c["pair_launch_timeouts"] == 0 and "pair_launches_note" in c, c
     assert d["value"] > 0 and d["steps"] == 3
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step computed, float32, within 64 MB: the same arrays on two runs with the
+    same arguments (seeded inputs and parameters; equal up to the order of float atomics: 1e-3 relative after 38 steps), and a later
+    training state when --steps asks for one more timed step (Adam moves the parameters by ~lr each)."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(tag, steps):
+        d = tmp_path / tag
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "1", "--no-infer",
+                              "--no-cpu-baseline", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, cwd=root)
+        assert out.returncode == 0, out.stderr[-3000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == steps and line["config"]["pair_launch_timeouts"] == 0
+        files = sorted(d.iterdir())
+        assert sum(f.stat().st_size for f in files) <= 64 * 10 ** 6
+        got = {f.stem: np.load(f) for f in files}
+        for k, a in got.items():
+            assert a.dtype == np.float32 and np.isfinite(a).all(), k
+        return got
+
+    a, b, c = run("a", 2), run("b", 2), run("c", 3)
+    names = {"decoded", "loss_time", "loss_freq", "params", "grads", "loss_quan_scope_1", "loss_quan_scope_2", "entropy_scope_1",
+             "entropy_scope_2", "loss_quan_lpc"}
+    assert names <= set(a) and set(a) == set(b) == set(c)
+    assert a["decoded"].shape == (128, 1, 512) and a["loss_time"].shape == (128,) and a["params"].shape == a["grads"].shape
+    for k in a:
+        x, y = a[k].astype(np.float64), b[k].astype(np.float64)
+        assert np.linalg.norm(x - y) <= 1e-2 * max(np.linalg.norm(x), 1e-30), k
+    same = float(np.abs(b["params"] - a["params"]).mean())
+    later = float(np.abs(c["params"] - a["params"]).mean())
+    assert later > 1e-5 and later > 10 * same, (later, same)

@@ -347,6 +347,45 @@ def test_bench_starts_its_own_ranks_when_asked_for_more_than_one_gpu():
         assert r.returncode != 0 and '"metric"' not in r.stdout
 
 
+def test_bench_times_exactly_the_steps_asked_for():
+    """`--steps K` is the number of timed steps: the passes add up to K, there are at most --passes of them, and none is shorter than
+    MIN_PASS_STEPS unless K is."""
+    import bench
+    for k in range(1, 200):
+        for passes in (1, 2, 3, 7):
+            s = bench.pass_sizes(k, passes)
+            assert sum(s) == k and 1 <= len(s) <= passes and max(s) - min(s) <= 1, (k, passes, s)
+            assert min(s) >= min(k, bench.MIN_PASS_STEPS), (k, passes, s)
+    assert bench.pass_sizes(30, 3) == [10, 10, 10]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
+
+def test_bench_dump_outputs_stay_within_budget_and_sample_reproducibly(tmp_path, monkeypatch):
+    """dump_outputs writes float32 <name>.npy files; small arrays whole, and when the budget is short the largest arrays are replaced by
+    the same seeded sample on every call, all files together within DUMP_BYTES."""
+    import bench
+    rng = np.random.default_rng(0)
+    arrays = {"small": rng.standard_normal(7).astype(np.float32), "mid": rng.standard_normal((3, 4, 5)),
+              "big": rng.standard_normal(400_000).astype(np.float32), "bigger": rng.standard_normal(600_000).astype(np.float32)}
+    done = bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "all" / f"{name}.npy")
+        assert got.dtype == np.float32 and done[name] == (a.shape, True)
+        assert np.array_equal(got, a.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2_000_000)
+    runs = []
+    for d in ("s1", "s2"):
+        done = bench.dump_outputs(str(tmp_path / d), arrays)
+        files = sorted((tmp_path / d).iterdir())
+        assert sum(f.stat().st_size for f in files) <= bench.DUMP_BYTES
+        assert done["small"][1] and done["mid"][1] and not done["big"][1] and not done["bigger"][1]
+        runs.append({f.stem: np.load(f) for f in files})
+    for name in arrays:
+        assert runs[0][name].dtype == np.float32 and np.array_equal(runs[0][name], runs[1][name]), name
+    assert np.isin(runs[0]["big"], arrays["big"]).all() and runs[0]["big"].size > 100_000
+
+
 def test_comm_refuses_rccl_with_fewer_gpus_than_local_ranks(monkeypatch):
     """First-contact robustness: RCCL with two ranks on one device fails deep inside the first collective; Comm says so up front."""
     from nsc_amd import dist as D
